@@ -8,15 +8,24 @@ of the hot path over the batch: qsmd5_hash_batch_device_async (the gfx950
 kernel) producing all 512 digests, plus, for N > 1 GPUs, the RCCL all-gather
 of the 16-byte digests (rank r holds parts [512 r, 512 (r+1)) of the job).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
-prints ONE JSON line (rank 0) with value = whole-job GiB/s hashed, the
-roofline of the dominant kernel (HIP events on the launch stream) and the CPU
-baseline (the reference's own md5() built from /root/reference into
-oracle/_ref, or the oracle port if that build is absent) timed on this host's
-cores over the same 512 chunks -- which also re-checks every GPU digest
-against the reference on the box.  Digests are checked against the committed
-golden fixture (tests/golden/batch_10MiB.json) every run.
+prints ONE JSON line (rank 0) with value = whole-job GiB/s hashed over the K
+timed steps, ms_per_step, and the roofline arithmetic of the dominant kernel
+(HIP events on the launch stream).  A plain run does only that: set up, warm
+up, time the K steps, print.  --dump-outputs DIR also writes what the last
+timed step returned, the job's digest table, as DIR/digests.npy (float32,
+one row of 16 byte values per chunk); the input is the same LCG stream every
+run, so two builds can be compared digest for digest.
+
+--full adds everything else, each in a run of its own after the timed steps:
+the parity check of the first and last timed step's digests against the
+committed golden fixture (tests/golden/batch_10MiB.json; a mismatch exits 3),
+the HBM traffic and clock evidence read from profiles/, the process group's
+report, the CPU baseline (the reference's own md5() where build() compiled it
+into oracle/_ref, or the oracle port if that build is absent) timed on this
+host's cores over the same 512 chunks -- which also re-checks every GPU digest
+against the reference on the box -- and the config5_host key.
 """
 import argparse
 import ctypes
@@ -354,7 +363,12 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=BATCH, help="chunks per GPU (default 512)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's digest table to DIR/digests.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the parity check, the CPU baseline, the "
+                         "config5_host leg and the profile/process-group report (off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--dist-always", action="store_true",
                     help="init the process group and gather digests even at world size 1 "
                          "(exercises the RCCL path on a 1-GPU box)")
@@ -369,6 +383,8 @@ def main():
                     help="no GPU: run only the config5_host leg on CPU ranks over gloo (numpy "
                          "parts, libqsmd5's CPU backend) and print its JSON line")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and not launched():
         # A bare `bench.py --gpus N` (the driver's command): form the N ranks here,
@@ -475,18 +491,27 @@ def main():
     kernel_ms = [a.elapsed_time(b) for a, b in events]
     kavg_ms = sum(kernel_ms) / len(kernel_ms)
 
-    # --- parity: every digest of the job against the reference-produced fixture -------
-    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "batch_10MiB.json")))["md5"]
-    table = out
-    got_hex = [bytes(r).hex() for r in table.cpu().numpy()]
-    first_hex = [bytes(r).hex() for r in first.cpu().numpy()]
     ntot = B * world
-    parity_ok = ntot <= len(gold) and got_hex[:ntot] == gold[:ntot] and first_hex[:ntot] == gold[:ntot]
-    if rank == 0 and not parity_ok:
-        bad = [i for i in range(min(ntot, len(gold))) if got_hex[i] != gold[i]]
-        log("PARITY FAILURE: %d of %d digests differ (first %s)" % (len(bad), ntot, bad[:5]))
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the job's
+        # digest table (for N > 1 the gathered one), one row of 16 bytes per chunk
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "digests.npy"),
+                out.cpu().numpy()[:ntot].astype(np.float32))
 
-    pg = group_report(B, dev) if distributed else None
+    # --- parity (--full): every digest of the job against the reference-produced fixture
+    parity_ok, got_hex = True, None
+    if args.full:
+        gold = json.load(open(os.path.join(ROOT, "tests", "golden", "batch_10MiB.json")))["md5"]
+        got_hex = [bytes(r).hex() for r in out.cpu().numpy()]
+        first_hex = [bytes(r).hex() for r in first.cpu().numpy()]
+        parity_ok = ntot <= len(gold) and got_hex[:ntot] == gold[:ntot] and first_hex[:ntot] == gold[:ntot]
+        if rank == 0 and not parity_ok:
+            bad = [i for i in range(min(ntot, len(gold))) if got_hex[i] != gold[i]]
+            log("PARITY FAILURE: %d of %d digests differ (first %s)" % (len(bad), ntot, bad[:5]))
+
+    pg = group_report(B, dev) if distributed and args.full else None
     job_bytes = float(ntot) * L
     value = job_bytes / (1 << 30) / elapsed * args.steps
     ms_per_step = elapsed / args.steps * 1e3
@@ -511,7 +536,7 @@ def main():
                    if world > 1 else "single GPU", "kernel": kernel},
         "roofline": {"bound": "hbm", "achieved": round(achieved_gbs, 2), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved_gbs / HBM_PEAK_GBS, 5),
-                     "traffic": _traffic_from_profiles(),
+                     "traffic": _traffic_from_profiles() if args.full else None,
                      "kernel_ms_avg": round(kavg_ms, 3),
                      "algorithmic_bytes_per_launch": B * L},
         # the stream-parallelism ceiling beside % of HBM peak.  A chunk
@@ -535,8 +560,9 @@ def main():
                       "cycles_per_64B_block_at_2p4GHz": round(kavg_ms * 1e-3 * 2.4e9 / (L / 64), 1),
                       "note": "MD5 is a serial chain per chunk; at batch=512 the job rate is "
                               "512 x the per-chain rate (SURVEY.md §0 item 5)",
-                      "clock_evidence": _clock_evidence()},
-        "parity": "ok: %d/%d digests == reference golden" % (ntot, ntot) if parity_ok else "FAIL",
+                      "clock_evidence": _clock_evidence() if args.full else None},
+        "parity": ("ok: %d/%d digests == reference golden" % (ntot, ntot) if parity_ok else "FAIL")
+        if args.full else "not checked (a plain run; --full checks it)",
         "process_group": pg,
         "cpu_baseline": None,
     }
@@ -544,7 +570,7 @@ def main():
         result["launcher"] = ("bench.py: %d child processes, one per GPU" % world
                               if os.environ.get("QSMD5_SPAWNED_BY") == "bench" else
                               "external (torch.distributed.run or equivalent)")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         host = data.cpu().numpy()
         chunks = [host[i * L:(i + 1) * L].ctypes.data for i in range(B)]
         cb = cpu_baseline(chunks, got_hex[:B], round(value, 3))
@@ -552,10 +578,10 @@ def main():
         if not cb["agrees_with_gpu"]:
             result["parity"] = "FAIL (cpu reference disagrees)"
         del host
-    del data, desc, digs, out, first, table
+    del data, desc, digs, out, first
     torch.cuda.empty_cache()
     c5_ok = True
-    if not args.no_config5:
+    if args.full and not args.no_config5:
         # the host-resident object, strong-scaled over the ranks (extra key; the
         # headline above is unchanged)
         result["config5_host"], c5_ok = config5_host_leg(args, rank, world, dev)

@@ -14,7 +14,7 @@ mkdir -p "$OUT"
 cd /tmp
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench" -o bench -- \
-  python3 "$R/bench.py" > "$OUT/bench.json" 2> "$OUT/bench.err"
+  python3 "$R/bench.py" --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_bench" -o pmc -- \
   python3 "$R/bench.py" --no-cpu-baseline --no-config5 --steps 2 --warmup 1 > "$OUT/pmc_bench.json" 2> "$OUT/pmc_bench.err"
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_calib" -o pmc -- \

@@ -252,7 +252,7 @@ def test_bench_two_rank_rehearsal():
     cmd = [PY, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "64", "--rehearse-gloo", "--config5-parts", "40", "--config5-reps", "1"]
+           "--batch", "64", "--rehearse-gloo", "--full", "--config5-parts", "40", "--config5-reps", "1"]
     out = subprocess.run(cmd, env=ENV, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -275,7 +275,7 @@ def test_bench_rehearsal_rank_without_parts():
     cmd = [PY, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "1", "--warmup", "1",
-           "--batch", "16", "--rehearse-gloo", "--config5-parts", "2", "--config5-reps", "1",
+           "--batch", "16", "--rehearse-gloo", "--full", "--config5-parts", "2", "--config5-reps", "1",
            "--config5-warmup", "0"]
     out = subprocess.run(cmd, env=ENV, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
@@ -296,7 +296,7 @@ def test_bench_rccl_path_world_one():
     cmd = [PY, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--batch", "64", "--dist-always", "--no-cpu-baseline", "--config5-parts", "32",
+           "--batch", "64", "--dist-always", "--full", "--no-cpu-baseline", "--config5-parts", "32",
            "--config5-reps", "1"]
     out = subprocess.run(cmd, env=ENV, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
@@ -326,7 +326,7 @@ def test_bench_forms_two_ranks_itself_on_the_card():
     item 1): bench.py starts both rank processes itself; they share the box's
     one card over gloo and the group reports two ranks."""
     cmd = [PY, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "64", "--rehearse-gloo", "--config5-parts", "40", "--config5-reps", "1"]
+           "--batch", "64", "--rehearse-gloo", "--full", "--config5-parts", "40", "--config5-reps", "1"]
     out = subprocess.run(cmd, env=_bare_env(), capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -343,8 +343,8 @@ def test_bench_parity_checks_the_timed_steps_own_digests():
     """the digest tables are zeroed after the warm-up and
     the first and last timed steps write to different tables, so parity holds
     only if the timed launches themselves produced every digest."""
-    cmd = [PY, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-config5",
-           "--no-cpu-baseline"]
+    cmd = [PY, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full",
+           "--no-config5", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=_bare_env(), capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -352,3 +352,30 @@ def test_bench_parity_checks_the_timed_steps_own_digests():
     r = json.loads(lines[0])
     assert r["n_gpus"] == 1 and r["parity"] == "ok: 512/512 digests == reference golden"
     assert "launcher" not in r  # the N = 1 line keeps BENCH_r03's keys
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_steps_digests(tmp_path, golden):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times its steps and
+    prints the headline line, nothing else: no CPU baseline, no config5_host
+    leg, no parity pass.  --dump-outputs writes the last timed step's digest
+    table (float32, one row of 16 byte values per chunk), which matches the
+    reference-produced golden table digest for digest."""
+    import numpy as np
+    out_dir = tmp_path / "dump"
+    cmd = [PY, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--batch", "64", "--dump-outputs", str(out_dir)]
+    out = subprocess.run(cmd, env=_bare_env(), capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["n_gpus"] == 1
+    assert r["unit"] == "GiB/s" and r["higher_is_better"] is True and r["dtype"] == "u32"
+    assert r["ms_per_step"] > 0
+    # value and ms_per_step describe the same timed steps
+    assert abs(r["value"] - 64 * 10 / 1024.0 / (r["ms_per_step"] * 1e-3)) <= 0.01 * r["value"]
+    assert r["cpu_baseline"] is None and "config5_host" not in r
+    assert r["parity"].startswith("not checked")
+    d = np.load(out_dir / "digests.npy")
+    assert d.dtype == np.float32 and d.shape == (64, 16)
+    assert [bytes(row).hex() for row in d.astype(np.uint8)] == golden("batch_10MiB.json")["md5"][:64]
