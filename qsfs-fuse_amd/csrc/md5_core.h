@@ -110,6 +110,24 @@ __device__ __forceinline__ void md5_steps_mk(uint32_t (&v)[4], const uint32_t (&
   }
 }
 
+// The same steps with mk held in SGPRs (scalar-fed latency kernel): m holds
+// mk[kBase .. kBase + 32), wave-uniform, and is the one scalar operand that
+// v_add3_u32 may take.
+typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+template <int I, int kEnd, int kBase>
+__device__ __forceinline__ void md5_steps_mk(uint32_t (&v)[4], const u32x16 (&m)[2]) {
+  if constexpr (I < kEnd) {
+    static_assert(I >= kBase && kEnd <= kBase + 32, "m covers 32 steps from kBase");
+    constexpr int ia = (4 - (I & 3)) & 3;
+    constexpr int ib = (ia + 1) & 3;
+    constexpr int ic = (ia + 2) & 3;
+    constexpr int id = (ia + 3) & 3;
+    const uint32_t t = v[ia] + md5_round_fn<I>(v[ib], v[ic], v[id]) + m[(I - kBase) >> 4][(I - kBase) & 15];
+    v[ia] = v[ib] + __builtin_rotateleft32(t, md5_shift(I));
+    md5_steps_mk<I + 1, kEnd, kBase>(v, m);
+  }
+}
+
 __device__ __forceinline__ void md5_compress_mk(uint32_t (&st)[4], const uint32_t (&mk)[64]) {
   uint32_t v[4] = {st[0], st[1], st[2], st[3]};
   md5_steps_mk<0>(v, mk);

@@ -9,6 +9,15 @@
 //                            the serial 4-VALU steps.  qsmd5_batch_pc64/32_kernel
 //                            are the same with 64 / 32 chains per workgroup
 //                            fixed at compile time (what the runtime launches).
+//   qsmd5_batch_sf_kernel    scalar-fed latency kernel, <= 512 chunks (the
+//                            headline batch): one chain per wave, 3 chain
+//                            waves + 1 producer wave per workgroup; the
+//                            producer writes x[g]+K to a ring in global
+//                            memory and the chain waves read it into SGPRs
+//                            (s_load_dwordx16 glc), so a step's v_add3 takes
+//                            it as its scalar operand and no LDS read is
+//                            left in the chain.  A sub-mode of the latency
+//                            kernel (launch_batch, QSMD5_PC_FEED).
 //   qsmd5_batch_pc2_kernel   the same with a 64 KiB ring (two workgroups per
 //                            CU): <= 2 x 256 x 64 chunks.
 //   qsmd5_batch_coal_kernel  throughput kernel, more chunks, 16-B aligned:
@@ -31,7 +40,9 @@
 // set by the dependent instructions per block (4 per step, 256 per block at
 // best), not by lanes per wave: 64 chains share one wave at no cost per chain
 // and leave the other SIMDs free.  Batch workgroups each own 64 chunks, so the
-// dispatcher spreads them over all 8 XCDs / 256 CUs.
+// dispatcher spreads them over all 8 XCDs / 256 CUs.  The scalar-fed kernel
+// turns this round for small batches: with at most one chain wave per SIMD, a
+// chain per wave costs nothing either, and its operands can live in SGPRs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -678,6 +689,387 @@ extern "C" __global__ __launch_bounds__(128) void qsmd5_column_pc2_kernel(
   pc_body<true, 1, 2>(segs, order, n, digests, col_off, col_w, states, 0u);
 }
 
+// ---- scalar-fed latency kernel --------------------------------------------------
+// One chain per WAVE (every lane carries the same state), mk in SGPRs: v_add3_u32 takes mk as
+// its one scalar operand, so a block costs the chain wave 256 VALU plus 4
+// s_load_dwordx16 and 4/3 waits instead of pc_body's 16 ds_read_b128.
+// Workgroup = kSfChains chain waves + 1 producer wave over kSfChains chunks.
+// Producer lane (c, h) streams block p * kSfHalf + h of chain c and stores its
+// 64 mk words as one 256-byte record into a ring in GLOBAL memory (two halves
+// of kSfHalf records per chain); the chain wave reads the records with scalar
+// loads that carry glc, which miss the scalar cache and read the XCD's L2,
+// where the same CU's stores have landed once vmcnt has drained.  Waves meet
+// only at s_barrier inside the workgroup: barrier p + 1 says "phase p + 1 is
+// written, and phase p has been read".
+constexpr int kSfChains = 3;  // + the producer: one wave per SIMD
+constexpr int kSfHalf = 3;    // blocks per phase: 192 steps = 4 SGPR loads of 48 steps
+constexpr int kSfLanes = 4;   // producer lanes per chain (kSfHalf of them at work)
+constexpr uint32_t kSfRecord = 256;      // bytes per block record
+constexpr uint32_t kSfHalfBytes = 1024;  // a ring half: kSfHalf records, padded to 1 KiB
+constexpr uint32_t kSfRingBytes = 2 * kSfHalfBytes;  // 2 KiB per chain
+constexpr uint32_t kSfThreads = (kSfChains + 1) * 64;
+
+// Ragged phases only: mk[kOff/4 .. kOff/4 + 32) of a record into 32 SGPRs,
+// load and wait in one statement, so the registers are valid wherever the
+// compiler may touch them.  Scalar loads return out of order: lgkmcnt(0) is
+// the only usable wait.
+template <int kOff>
+__device__ __forceinline__ void sf_fetch(u32x16 (&m)[2], const uint8_t* rec) {
+  asm volatile(
+      "s_load_dwordx16 %0, %2, %3 glc\n\t"
+      "s_load_dwordx16 %1, %2, %4 glc\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&s"(m[0]), "=&s"(m[1])
+      : "s"(rec), "n"(kOff), "n"(kOff + 64)
+      : "memory");
+}
+
+// A ragged phase of a chain wave (the chain owns only some of its blocks, or
+// none): block by block, the loads' latency exposed, then the phase barrier.
+__device__ __forceinline__ void sf_chain_ragged(uint32_t (&st)[4], const uint8_t* cur,
+                                                uint32_t blk0, uint32_t nblk) {
+  for (uint32_t h = 0; h < (uint32_t)kSfHalf; ++h) {
+    if (blk0 + h < nblk) {  // blk0 may wrap (skew)
+      u32x16 m[2];
+      uint32_t v[4] = {st[0], st[1], st[2], st[3]};
+      sf_fetch<0>(m, cur + h * kSfRecord);
+      md5_steps_mk<0, 32, 0>(v, m);
+      sf_fetch<128>(m, cur + h * kSfRecord);
+      md5_steps_mk<32, 64, 32>(v, m);
+      st[0] += v[0];
+      st[1] += v[1];
+      st[2] += v[2];
+      st[3] += v[3];
+    }
+  }
+  asm volatile("s_barrier" ::: "memory");
+}
+
+// The run of whole phases, written out: between a scalar load and its wait the
+// destination SGPRs hold nothing the compiler may copy or spill, so the loop
+// owns its registers outright: s2 phases left, vcc the ring half, and two
+// sets of 48 mk words, X = s[4:51] and Y = s[52:99].  The 192 steps of a phase
+// (3 blocks) are 4 loads of 48 steps, at 192-byte strides through the half.
+// While one set's 48 steps run (~800 cycles), the other set's 3
+// s_load_dwordx16 are in flight; scalar loads return out of order, so the only
+// usable wait is lgkmcnt(0), and a load's lead is one set's run.  (Sets of 32
+// steps, ~530 cycles, were not enough with 512 chains at work: 1536 cycles
+// per block against 1115 with 256, profiles/r07_scalar_feed.log.)  The phase
+// barrier sits where the last load of this ring half has landed, 16 steps into
+// the last block; the first load of the other half follows it.
+// A step is v_bitop3 (F/G/H/I) + v_add3 (a + mk + f) + v_alignbit (rotate) +
+// v_add (+ b); the first four steps of a block read the state registers and
+// write the working ones, so no copy is needed.
+#define SF_STEP(AI, AO, B, C, D, MK, ROTR, IMM)                \
+  "v_bitop3_b32 %[t], " B ", " C ", " D " bitop3:" IMM "\n\t"  \
+  "v_add3_u32 %[t], " AI ", " MK ", %[t]\n\t"                  \
+  "v_alignbit_b32 %[t], %[t], %[t], " ROTR "\n\t"              \
+  "v_add_u32_e32 " AO ", %[t], " B "\n\t"
+#define SF_S0 "%[s0]"
+#define SF_S1 "%[s1]"
+#define SF_S2 "%[s2]"
+#define SF_S3 "%[s3]"
+#define SF_V0 "%[v0]"
+#define SF_V1 "%[v1]"
+#define SF_V2 "%[v2]"
+#define SF_V3 "%[v3]"
+#define SF_R4(M0, M1, M2, M3, R0, R1, R2, R3, IMM)              \
+  SF_STEP(SF_V0, SF_V0, SF_V1, SF_V2, SF_V3, M0, R0, IMM)       \
+  SF_STEP(SF_V3, SF_V3, SF_V0, SF_V1, SF_V2, M1, R1, IMM)       \
+  SF_STEP(SF_V2, SF_V2, SF_V3, SF_V0, SF_V1, M2, R2, IMM)       \
+  SF_STEP(SF_V1, SF_V1, SF_V2, SF_V3, SF_V0, M3, R3, IMM)
+// steps 0-3 of a block: from the state registers into the working ones
+#define SF_F0(M0, M1, M2, M3)                                        \
+  SF_STEP(SF_S0, SF_V0, SF_S1, SF_S2, SF_S3, M0, "25", "0xca")       \
+  SF_STEP(SF_S3, SF_V3, SF_V0, SF_S1, SF_S2, M1, "20", "0xca")       \
+  SF_STEP(SF_S2, SF_V2, SF_V3, SF_V0, SF_S1, M2, "15", "0xca")       \
+  SF_STEP(SF_S1, SF_V1, SF_V2, SF_V3, SF_V0, M3, "10", "0xca")
+#define SF_F(M0, M1, M2, M3) SF_R4(M0, M1, M2, M3, "25", "20", "15", "10", "0xca")
+#define SF_G(M0, M1, M2, M3) SF_R4(M0, M1, M2, M3, "27", "23", "18", "12", "0xe4")
+#define SF_H(M0, M1, M2, M3) SF_R4(M0, M1, M2, M3, "28", "21", "16", "9", "0x96")
+#define SF_I(M0, M1, M2, M3) SF_R4(M0, M1, M2, M3, "26", "22", "17", "11", "0x39")
+#define SF_FF                                 \
+  "v_add_u32_e32 %[s0], %[s0], %[v0]\n\t"     \
+  "v_add_u32_e32 %[s1], %[s1], %[v1]\n\t"     \
+  "v_add_u32_e32 %[s2], %[s2], %[v2]\n\t"     \
+  "v_add_u32_e32 %[s3], %[s3], %[v3]\n\t"
+#define SF_LOAD_X(O0, O1, O2)                             \
+  "s_load_dwordx16 s[4:19], vcc, " O0 " glc\n\t"   \
+  "s_load_dwordx16 s[20:35], vcc, " O1 " glc\n\t"  \
+  "s_load_dwordx16 s[36:51], vcc, " O2 " glc\n\t"
+#define SF_LOAD_Y(O0, O1, O2)                             \
+  "s_load_dwordx16 s[52:67], vcc, " O0 " glc\n\t"  \
+  "s_load_dwordx16 s[68:83], vcc, " O1 " glc\n\t"  \
+  "s_load_dwordx16 s[84:99], vcc, " O2 " glc\n\t"
+#define SF_WAIT "s_waitcnt lgkmcnt(0)\n\t"
+// `half` is the ring half of the first phase; the other half is half ^ 1 KiB
+// (the chain's ring is 2 KiB-aligned).  nphases >= 1.  Ends with the barrier
+// of the last phase passed (and one unused load of the half after it).
+__device__ __forceinline__ void sf_chain_whole(uint32_t (&st)[4], const uint8_t* half,
+                                               uint32_t nphases) {
+  static_assert(kSfHalf == 3 && kSfRecord == 256 && kSfHalfBytes == 0x400, "offsets below");
+  uint32_t v0, v1, v2, v3, t;
+  asm volatile(
+      "s_mov_b32 s2, %[n]\n\t"
+      "s_mov_b64 vcc, %[half]\n\t"
+      SF_LOAD_X("0x0", "0x40", "0x80") SF_WAIT
+      "1:\n\t"
+      SF_LOAD_Y("0xc0", "0x100", "0x140")
+      // block 0: step i on s(4 + i)
+      SF_F0("s4", "s5", "s6", "s7") SF_F("s8", "s9", "s10", "s11")
+      SF_F("s12", "s13", "s14", "s15") SF_F("s16", "s17", "s18", "s19")
+      SF_G("s20", "s21", "s22", "s23") SF_G("s24", "s25", "s26", "s27")
+      SF_G("s28", "s29", "s30", "s31") SF_G("s32", "s33", "s34", "s35")
+      SF_H("s36", "s37", "s38", "s39") SF_H("s40", "s41", "s42", "s43")
+      SF_H("s44", "s45", "s46", "s47") SF_H("s48", "s49", "s50", "s51")
+      SF_WAIT SF_LOAD_X("0x180", "0x1c0", "0x200")
+      SF_I("s52", "s53", "s54", "s55") SF_I("s56", "s57", "s58", "s59")
+      SF_I("s60", "s61", "s62", "s63") SF_I("s64", "s65", "s66", "s67") SF_FF
+      // block 1: steps 0-31 on s(68 + i), steps 32-63 on s(i - 28)
+      SF_F0("s68", "s69", "s70", "s71") SF_F("s72", "s73", "s74", "s75")
+      SF_F("s76", "s77", "s78", "s79") SF_F("s80", "s81", "s82", "s83")
+      SF_G("s84", "s85", "s86", "s87") SF_G("s88", "s89", "s90", "s91")
+      SF_G("s92", "s93", "s94", "s95") SF_G("s96", "s97", "s98", "s99")
+      SF_WAIT SF_LOAD_Y("0x240", "0x280", "0x2c0")
+      SF_H("s4", "s5", "s6", "s7") SF_H("s8", "s9", "s10", "s11")
+      SF_H("s12", "s13", "s14", "s15") SF_H("s16", "s17", "s18", "s19")
+      SF_I("s20", "s21", "s22", "s23") SF_I("s24", "s25", "s26", "s27")
+      SF_I("s28", "s29", "s30", "s31") SF_I("s32", "s33", "s34", "s35") SF_FF
+      // block 2: step i on s(36 + i)
+      SF_F0("s36", "s37", "s38", "s39") SF_F("s40", "s41", "s42", "s43")
+      SF_F("s44", "s45", "s46", "s47") SF_F("s48", "s49", "s50", "s51")
+      SF_WAIT
+      "s_barrier\n\t"
+      "s_xor_b32 vcc_lo, vcc_lo, 0x400\n\t"
+      SF_LOAD_X("0x0", "0x40", "0x80")
+      SF_G("s52", "s53", "s54", "s55") SF_G("s56", "s57", "s58", "s59")
+      SF_G("s60", "s61", "s62", "s63") SF_G("s64", "s65", "s66", "s67")
+      SF_H("s68", "s69", "s70", "s71") SF_H("s72", "s73", "s74", "s75")
+      SF_H("s76", "s77", "s78", "s79") SF_H("s80", "s81", "s82", "s83")
+      SF_I("s84", "s85", "s86", "s87") SF_I("s88", "s89", "s90", "s91")
+      SF_I("s92", "s93", "s94", "s95") SF_I("s96", "s97", "s98", "s99") SF_FF
+      SF_WAIT
+      "s_add_i32 s2, s2, -1\n\t"
+      "s_cmp_lg_u32 s2, 0\n\t"
+      "s_cbranch_scc1 1b"
+      : [s0] "+v"(st[0]), [s1] "+v"(st[1]), [s2] "+v"(st[2]), [s3] "+v"(st[3]),
+        [v0] "=&v"(v0), [v1] "=&v"(v1), [v2] "=&v"(v2), [v3] "=&v"(v3), [t] "=&v"(t)
+      : [n] "s"(nphases), [half] "s"(half)
+      : "memory", "scc", "s2", "s4", "s5", "s6", "s7", "s8", "s9", "s10", "s11", "s12", "s13",
+        "s14", "s15", "s16", "s17", "s18", "s19", "s20", "s21", "s22", "s23", "s24", "s25", "s26",
+        "s27", "s28", "s29", "s30", "s31", "s32", "s33", "s34", "s35", "s36", "s37", "s38", "s39",
+        "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52",
+        "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65",
+        "s66", "s67", "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78",
+        "s79", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91",
+        "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99", "vcc");
+}
+#undef SF_WAIT
+#undef SF_LOAD_Y
+#undef SF_LOAD_X
+#undef SF_FF
+#undef SF_I
+#undef SF_H
+#undef SF_G
+#undef SF_F
+#undef SF_F0
+#undef SF_R4
+#undef SF_V3
+#undef SF_V2
+#undef SF_V1
+#undef SF_V0
+#undef SF_S3
+#undef SF_S2
+#undef SF_S1
+#undef SF_S0
+#undef SF_STEP
+
+// One block's 64 mk words -> row `lane` of the producer's LDS staging tile.
+// Rows are 17 x 16 B apart, so the 64 rows' ds_write_b128 spread over the banks.
+constexpr int kSfStageRow = 17;
+__device__ __forceinline__ void sf_stage_mk(u32x4 (*stage)[kSfStageRow], uint32_t lane,
+                                            const PcBlockRegs& r, uint32_t off) {
+  uint32_t d[17] = {r.q[0].x, r.q[0].y, r.q[0].z, r.q[0].w, r.q[1].x, r.q[1].y,
+                    r.q[1].z, r.q[1].w, r.q[2].x, r.q[2].y, r.q[2].z, r.q[2].w,
+                    r.q[3].x, r.q[3].y, r.q[3].z, r.q[3].w, r.e};
+  uint32_t w[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) w[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], off);
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    u32x4 m;
+    m.x = w[md5_word(4 * g + 0)] + Md5Tables::K[4 * g + 0];
+    m.y = w[md5_word(4 * g + 1)] + Md5Tables::K[4 * g + 1];
+    m.z = w[md5_word(4 * g + 2)] + Md5Tables::K[4 * g + 2];
+    m.w = w[md5_word(4 * g + 3)] + Md5Tables::K[4 * g + 3];
+    stage[lane][g] = m;
+  }
+}
+
+// The staged phase -> ring half `half` (0 / 1) of every chain of the workgroup,
+// coalesced: store i writes chain i's kSfHalf records in one piece (row = lane
+// of the record's producer = chain x kSfLanes + block).
+template <int kChains>
+__device__ __forceinline__ void sf_flush(const u32x4 (*stage)[kSfStageRow], uint32_t lane,
+                                         uint8_t* wg_ring, uint32_t half) {
+  static_assert(kSfHalf * kSfRecord <= 64 * 16, "one store instruction per chain");
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the rows are written (one wave: no barrier)
+  if (lane < kSfHalf * kSfRecord / 16u) {
+#pragma unroll
+    for (int i = 0; i < kChains; ++i) {
+      const u32x4 m = stage[kSfLanes * i + (lane >> 4)][lane & 15u];
+      uint8_t* dst = wg_ring + (uint32_t)i * kSfRingBytes + half * kSfHalfBytes + lane * 16u;
+      *(QS_GLOBAL u32x4*)(reinterpret_cast<uintptr_t>(dst)) = m;
+    }
+  }
+}
+
+// kChains chain waves (chunks) per workgroup, at most 64 / kSfLanes = 16.
+// ring: (workgroups x kChains) x kSfRingBytes of scratch, kSfRingBytes-aligned,
+// private to the launch.
+// kAgentFence: the producer publishes a phase behind a release fence of agent
+// scope (writes the L2's dirty lines back) instead of the bare vmcnt(0) wait.
+// kProbe (ubench attribution only, as in pc_body): bit 0 = the producer skips
+// its ring writes, bit 1 = it skips its global loads; the digests are then wrong.
+// skew: as in pc_body, per chain: chain t starts perm(t) x skew blocks late
+// when the workgroup's longest chunk has >= kSkewMinBlocks blocks.
+template <int kChains, int kDepth, bool kNT, bool kAgentFence, int kProbe = 0>
+__device__ __forceinline__ void sf_body(const ChunkDesc* __restrict__ chunks,
+                                        const uint32_t* __restrict__ order, uint32_t n,
+                                        uint32_t* __restrict__ digests, uint32_t skew,
+                                        uint8_t* ring) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = rfl_u32(threadIdx.x >> 6);
+  const bool producer = wave == (uint32_t)kChains;
+  // Every wave looks at all kChains chunks (lane l at chain l / kSfLanes), so
+  // all agree on the number of phases; a chain wave then keeps its own chunk.
+  const uint32_t c = lane / (uint32_t)kSfLanes;
+  const uint32_t t = blockIdx.x * (uint32_t)kChains + c;
+  uint32_t idx = 0;
+  ChunkDesc cd = {nullptr, 0};
+  if (c < (uint32_t)kChains && t < n) {
+    idx = order ? order[t] : t;
+    cd = chunks[idx];
+  }
+  uint32_t nblk = (uint32_t)(cd.len >> 6);
+  const bool skewed = skew != 0 && wave_max_u32(nblk) >= kSkewMinBlocks;
+  uint32_t delta = (skewed && nblk) ? skew * ((t * 37u) & 63u) : 0u;
+  const uint32_t phases = rfl_u32((wave_max_u32(nblk + delta) + kSfHalf - 1) / kSfHalf);
+  uint8_t* const wg_ring = ring + (uint64_t)blockIdx.x * (kChains * kSfRingBytes);
+
+  if (producer) {
+    const uint32_t h = lane % (uint32_t)kSfLanes;  // block of the phase; h >= kSfHalf idles
+    const bool work = nblk != 0 && h < (uint32_t)kSfHalf;
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(cd.ptr);
+    const uint32_t off = (uint32_t)(pa & 3u);
+    const uint32_t* base = reinterpret_cast<const uint32_t*>(pa & ~uintptr_t(3));
+    const uint32_t last = nblk ? nblk - 1 : 0;
+    __shared__ u32x4 stage[64][kSfStageRow];
+    PcBlockRegs r[kDepth];
+    if constexpr ((kProbe & 2) != 0) {
+#pragma unroll
+      for (int k = 0; k < kDepth; ++k) r[k] = PcBlockRegs{{lane, lane, lane, lane}, lane};
+    }
+    auto load_phase = [&](PcBlockRegs& rs, uint32_t p) {
+      if constexpr ((kProbe & 2) != 0) return;
+      if (work) {
+        const uint32_t j = p * kSfHalf + h;  // virtual block; the chain's block is j - delta
+        pc_load_block<kNT>(rs, base, off, j < delta ? 0u : min(j - delta, last));
+      }
+    };
+    // The stores of a phase must have reached L2 before the barrier that
+    // publishes them; loads and stores share vmcnt, so the wait comes before
+    // the next prefetch is sent, which then has a whole phase to land.
+    auto write_phase = [&](const PcBlockRegs& rs, uint32_t p) {
+      if constexpr ((kProbe & 1) == 0) {
+        if (work) sf_stage_mk(stage, lane, rs, off);
+        sf_flush<kChains>(stage, lane, wg_ring, p & 1u);
+      }
+      if constexpr (kAgentFence) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    };
+    if (phases > 0) {
+#pragma unroll
+      for (int k = 0; k < kDepth; ++k) load_phase(r[k], (uint32_t)k);
+      write_phase(r[0], 0);
+      load_phase(r[0], kDepth);
+    }
+    asm volatile("s_barrier" ::: "memory");
+    for (uint32_t p0 = 0; p0 < phases; p0 += kDepth) {
+#pragma unroll
+      for (int u = 0; u < kDepth; ++u) {
+        const uint32_t p = p0 + (uint32_t)u;
+        if (p < phases) {
+          if (p + 1 < phases) {
+            write_phase(r[(u + 1) % kDepth], p + 1);
+            load_phase(r[(u + 1) % kDepth], p + 1 + kDepth);
+          }
+          asm volatile("s_barrier" ::: "memory");
+        }
+      }
+    }
+    return;
+  }
+
+  // ---------------- chain: this wave's chunk, the same in every lane ----------------
+  // All 64 lanes stay live and carry the same state: with one live lane the
+  // same step runs at 5.4 cycles per instruction instead of 4.14, and at 20
+  // with four such waves on a CU (profiles/r07_scalar_feed.log, step_feed).
+  const uint32_t my_t = blockIdx.x * (uint32_t)kChains + wave;
+  const uint32_t src = wave * (uint32_t)kSfLanes;  // a lane that holds this chain's chunk
+  idx = (uint32_t)__builtin_amdgcn_readlane((int)idx, src);
+  nblk = (uint32_t)__builtin_amdgcn_readlane((int)nblk, src);
+  delta = (uint32_t)__builtin_amdgcn_readlane((int)delta, src);
+  const uint32_t ptr_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)reinterpret_cast<uintptr_t>(cd.ptr), src);
+  const uint32_t ptr_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(reinterpret_cast<uintptr_t>(cd.ptr) >> 32), src);
+  const uint32_t len_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)cd.len, src);
+  const uint32_t len_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(cd.len >> 32), src);
+  const uint8_t* const ptr = reinterpret_cast<const uint8_t*>(((uint64_t)ptr_hi << 32) | ptr_lo);
+  const uint64_t len = ((uint64_t)len_hi << 32) | len_lo;
+  const uint8_t* const my = wg_ring + wave * kSfRingBytes;
+  // phases whose kSfHalf blocks all belong to the chain run without predicates
+  const uint32_t live_lo = (delta + kSfHalf - 1) / kSfHalf;
+  const uint32_t live_hi = (nblk + delta) / kSfHalf;
+  {
+    uint32_t st[4];
+    // through a VGPR the compiler cannot see into: the state must live in vector
+    // registers (a wave-uniform chain would otherwise be scalarised)
+    asm volatile("v_mov_b32 %0, %1" : "=v"(st[0]) : "s"(kInit0));
+    asm volatile("v_mov_b32 %0, %1" : "=v"(st[1]) : "s"(kInit1));
+    asm volatile("v_mov_b32 %0, %1" : "=v"(st[2]) : "s"(kInit2));
+    asm volatile("v_mov_b32 %0, %1" : "=v"(st[3]) : "s"(kInit3));
+    asm volatile("s_barrier" ::: "memory");  // phase 0 is written
+    // Every phase ends with its barrier, whichever way it ran: phases + 1
+    // barriers in all, as in the producer.
+    uint32_t p = 0;
+    while (p < phases) {
+      const uint8_t* cur = my + (p & 1u) * kSfHalfBytes;
+      if (p >= live_lo && p < live_hi) {
+        sf_chain_whole(st, cur, live_hi - p);
+        p = live_hi;
+      } else {
+        sf_chain_ragged(st, cur, p * kSfHalf - delta, nblk);
+        ++p;
+      }
+    }
+    if (my_t < n) {
+      finish(st, ptr + ((uint64_t)nblk << 6), (uint32_t)(len & 63u), len);
+      u32x4 o = {st[0], st[1], st[2], st[3]};
+      if (lane == 0) *reinterpret_cast<u32x4*>(digests + 4u * (uint64_t)idx) = o;
+    }
+  }
+}
+
+#define QSMD5_SF_KERNEL(NAME, NT, FENCE)                                                      \
+  extern "C" __global__ __launch_bounds__(kSfThreads) void NAME(                              \
+      const ChunkDesc* __restrict__ chunks, const uint32_t* __restrict__ order, uint32_t n,   \
+      uint32_t* __restrict__ digests, uint32_t skew, uint8_t* ring) {                         \
+    sf_body<kSfChains, kPcDepth, NT, FENCE>(chunks, order, n, digests, skew, ring);                      \
+  }
+QSMD5_SF_KERNEL(qsmd5_batch_sf_kernel, false, false)
+QSMD5_SF_KERNEL(qsmd5_batch_sf_nt_kernel, true, false)
+#undef QSMD5_SF_KERNEL
+
 // ---------------------------------------------------------------------------
 // Throughput kernel with coalesced LDS-DMA staging (batches of >> 16 K chunks).
 //
@@ -937,6 +1329,11 @@ extern "C" __global__ __launch_bounds__(256) void qsmd5_gather_kernel(const Gath
 // Host launchers (md5_launch.h).
 #include "md5_launch.h"
 
+#include <stdlib.h>
+#include <string.h>
+
+#include <mutex>
+
 namespace qsmd5 {
 
 // Each launcher returns hipGetLastError() after its launch, and that reports
@@ -946,6 +1343,90 @@ namespace qsmd5 {
 // clears it first (clear_stale_error), and the launch's own status is what
 // comes back.
 static inline void clear_stale_error() { (void)hipGetLastError(); }
+
+// Feed of the 64-lane latency kernel: the scalar-fed kernel up to
+// kScalarFedMaxChunks, where one chain per wave still fits beside the others;
+// QSMD5_PC_FEED=lds|sgpr overrides (read per call, so a process can A/B).
+static bool scalar_feed_for(uint32_t n) {
+  const char* e = getenv("QSMD5_PC_FEED");
+  if (e && !strcmp(e, "lds")) return false;
+  if (n > kScalarFedMaxChunks) return false;
+  if (e && !strcmp(e, "sgpr")) return true;
+  return kScalarFedDefault;
+}
+
+// Ring scratch of the scalar-fed kernel: slabs of kScalarFedMaxChunks rings that
+// the library keeps.  A launch takes a slab that no earlier launch still uses
+// (its event, recorded behind that launch, has completed), so concurrent
+// callers never share scratch and the call stays enqueue-only once the slabs
+// exist; a new slab costs one hipMalloc.  Scratch from hipMallocAsync /
+// hipFreeAsync on the caller's stream gave wrong digests with several host
+// threads hashing small buffers at once (tests/cpp/race_stress.cpp), which
+// is why the slabs are managed here.
+struct SfSlab {
+  void* raw = nullptr;
+  uint8_t* ring = nullptr;  // raw, kSfRingBytes-aligned
+  hipEvent_t done = nullptr;
+  int device = -1;
+  bool taken = false;  // between sf_acquire and sf_release
+};
+constexpr int kSfMaxSlabs = 32;
+static std::mutex g_sf_mu;
+static SfSlab g_sf_slabs[kSfMaxSlabs];
+
+static SfSlab* sf_acquire(hipStream_t s) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+    clear_stale_error();
+    return nullptr;  // neither hipMalloc nor hipEventQuery may run inside a capture
+  }
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) {
+    clear_stale_error();
+    return nullptr;
+  }
+  std::lock_guard<std::mutex> lk(g_sf_mu);
+  SfSlab* fresh = nullptr;
+  for (SfSlab& b : g_sf_slabs) {
+    if (!b.raw) {
+      if (!fresh) fresh = &b;
+      continue;
+    }
+    if (b.taken || b.device != dev) continue;
+    if (hipEventQuery(b.done) == hipSuccess) {
+      b.taken = true;
+      return &b;
+    }
+    clear_stale_error();  // hipErrorNotReady: an earlier launch still runs on it
+  }
+  if (!fresh) return nullptr;
+  constexpr size_t kChainsMax = (kScalarFedMaxChunks + kSfChains - 1) / kSfChains * kSfChains;
+  void* raw = nullptr;
+  hipEvent_t ev = nullptr;
+  if (hipMalloc(&raw, (kChainsMax + 1) * kSfRingBytes) != hipSuccess ||
+      hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+    if (raw) (void)hipFree(raw);
+    clear_stale_error();
+    return nullptr;
+  }
+  fresh->raw = raw;
+  fresh->ring = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(raw) + kSfRingBytes - 1) &
+                                           ~uintptr_t(kSfRingBytes - 1));
+  fresh->done = ev;
+  fresh->device = dev;
+  fresh->taken = true;
+  return fresh;
+}
+
+// After the launch on s: the slab is free again once everything enqueued on s
+// so far has run.  If the event cannot be recorded the slab is never handed
+// out again (it stays taken).
+static void sf_release(SfSlab* slab, hipStream_t s) {
+  const bool ok = hipEventRecord(slab->done, s) == hipSuccess;
+  if (!ok) clear_stale_error();
+  std::lock_guard<std::mutex> lk(g_sf_mu);
+  slab->taken = !ok;
+}
 
 hipError_t launch_batch(const void* chunks, const uint32_t* order, uint32_t n, uint32_t* digests,
                         int kind, hipStream_t s, uint32_t skew_blocks, bool load_nt, uint32_t lanes) {
@@ -957,6 +1438,17 @@ hipError_t launch_batch(const void* chunks, const uint32_t* order, uint32_t n, u
   if (kind == kKernelLatency) {
     const ChunkDesc* c = static_cast<const ChunkDesc*>(chunks);
     const uint32_t skew = skew_blocks / kPcHalf * kPcHalf;
+    if (lanes == 64 && scalar_feed_for(n)) {
+      if (SfSlab* slab = sf_acquire(s)) {
+        hipLaunchKernelGGL(load_nt ? qsmd5_batch_sf_nt_kernel : qsmd5_batch_sf_kernel,
+                           dim3((n + kSfChains - 1) / kSfChains), dim3(kSfThreads), 0, s, c, order, n,
+                           digests, skew, slab->ring);
+        const hipError_t e = hipGetLastError();
+        sf_release(slab, s);
+        return e;
+      }
+      // no scratch to be had: the LDS-fed kernel needs none
+    }
     if (lanes == 64)
       hipLaunchKernelGGL(load_nt ? qsmd5_batch_pc64_nt_kernel : qsmd5_batch_pc64_kernel,
                          dim3(pc_groups), dim3(128), 0, s, c, order, n, digests, skew);

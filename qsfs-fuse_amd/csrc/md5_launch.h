@@ -20,6 +20,17 @@ enum KernelKind : int {
 constexpr uint32_t kLatencyKernelResident = 256u * 64u;
 constexpr uint32_t kLatency2KernelResident = 2u * 256u * 64u;
 
+// Scalar-fed sub-mode of kKernelLatency (qsmd5_batch_sf_kernel: one chain per
+// wave, 3 chain waves + 1 producer wave per workgroup, one wave per SIMD):
+// chosen for 64-lane launches of at most kScalarFedMaxChunks chunks.  Measured
+// at 10 MiB chunks against the LDS-fed kernel: 1161 against 1194 cycles per
+// block at 512 chunks, 1203 against 1192 at 768 (every CU holds a workgroup and
+// the scalar loads queue), 2201 against 1187 at 1024, where workgroups share a
+// CU's SIMDs (profiles/r07_scalar_feed.log).
+// QSMD5_PC_FEED=lds keeps the LDS-fed kernel, =sgpr asks for this one.
+constexpr uint32_t kScalarFedMaxChunks = 512;
+constexpr bool kScalarFedDefault = true;
+
 // chunks: device array of {ptr,len}; order: optional device lane->chunk map;
 // digests: device, 16 B per chunk indexed by chunk index.
 // Start skew of the latency kernel for waves whose longest chunk is >= 32 MiB

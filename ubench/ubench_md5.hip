@@ -67,6 +67,192 @@ __global__ __launch_bounds__(128) void k_pc_probe(const ChunkDesc* __restrict__ 
       c, o, n, d, 0, ~0ull, nullptr, skew, nullptr, 64u);
 }
 
+// The scalar-fed latency kernel as shipped (kFence false) and with the producer
+// publishing each phase behind a release fence of agent scope.
+template <bool kFence>
+__global__ __launch_bounds__(kSfThreads) void k_sf(const ChunkDesc* __restrict__ c,
+                                                   const uint32_t* __restrict__ o, uint32_t n,
+                                                   uint32_t* __restrict__ d, uint32_t skew,
+                                                   uint8_t* ring) {
+  sf_body<kSfChains, kPcDepth, false, kFence>(c, o, n, d, skew, ring);
+}
+// ... with parts of its producer switched off (sf_body kProbe; digests wrong)
+template <int kProbe>
+__global__ __launch_bounds__(kSfThreads) void k_sf_attrib(const ChunkDesc* __restrict__ c,
+                                                          const uint32_t* __restrict__ o, uint32_t n,
+                                                          uint32_t* __restrict__ d, uint32_t skew,
+                                                          uint8_t* ring) {
+  sf_body<kSfChains, kPcDepth, false, false, kProbe>(c, o, n, d, skew, ring);
+}
+// ... and with kC chain waves per workgroup (shipped: 3, with the producer one wave per SIMD).
+template <int kC, int kProbe = 0>
+__global__ __launch_bounds__((kC + 1) * 64) void k_sfc(const ChunkDesc* __restrict__ c,
+                                                       const uint32_t* __restrict__ o, uint32_t n,
+                                                       uint32_t* __restrict__ d, uint32_t skew,
+                                                       uint8_t* ring) {
+  sf_body<kC, kPcDepth, false, false, kProbe>(c, o, n, d, skew, ring);
+}
+
+// Visibility probe for the scalar feed: one workgroup shaped like the scalar-fed
+// kernel.  Lap p, the producer wave overwrites ring half p & 1 of every chain
+// with a pattern of (p, chain, dword) -- the same addresses every other lap --
+// drains its stores (kFence: behind a release fence of agent scope) and arrives
+// at the barrier; each chain wave then reads its half with glc scalar loads and
+// counts the dwords that are not lap p's.  out[wave] = mismatches.
+__device__ __forceinline__ uint32_t sf_probe_word(uint32_t p, uint32_t c, uint32_t i) {
+  return (p + 1u) * 0x9E3779B1u + c * 4096u + i;
+}
+template <bool kFence>
+__global__ __launch_bounds__(kSfThreads) void k_sf_probe(uint8_t* ring, uint32_t laps,
+                                                         uint32_t* out) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = rfl_u32(threadIdx.x >> 6);
+  if (wave == (uint32_t)kSfChains) {
+    const uint32_t c = lane / kSfLanes, h = lane % kSfLanes;
+    auto write = [&](uint32_t p) {
+      if (c >= (uint32_t)kSfChains || h >= (uint32_t)kSfHalf) return;
+      QS_GLOBAL u32x4* rec = (QS_GLOBAL u32x4*)(reinterpret_cast<uintptr_t>(
+          ring + c * kSfRingBytes + (p & 1u) * kSfHalfBytes + h * kSfRecord));
+      for (uint32_t g = 0; g < 16; ++g) {
+        const uint32_t i = h * 64u + g * 4u;
+        rec[g] = u32x4{sf_probe_word(p, c, i), sf_probe_word(p, c, i + 1),
+                       sf_probe_word(p, c, i + 2), sf_probe_word(p, c, i + 3)};
+      }
+      if constexpr (kFence) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    };
+    write(0);
+    asm volatile("s_barrier" ::: "memory");
+    for (uint32_t p = 0; p < laps; ++p) {
+      if (p + 1 < laps) write(p + 1);
+      asm volatile("s_barrier" ::: "memory");
+    }
+    return;
+  }
+  uint32_t bad = 0;
+  asm volatile("s_barrier" ::: "memory");
+  for (uint32_t p = 0; p < laps; ++p) {
+    const uint8_t* half = ring + wave * kSfRingBytes + (p & 1u) * kSfHalfBytes;
+    for (uint32_t h = 0; h < (uint32_t)kSfHalf; ++h) {
+      u32x16 m[2];
+      sf_fetch<0>(m, half + h * kSfRecord);
+      for (int k = 0; k < 32; ++k) bad += m[k >> 4][k & 15] != sf_probe_word(p, wave, h * 64u + k);
+      sf_fetch<128>(m, half + h * kSfRecord);
+      for (int k = 0; k < 32; ++k)
+        bad += m[k >> 4][k & 15] != sf_probe_word(p, wave, h * 64u + 32u + k);
+    }
+    asm volatile("s_barrier" ::: "memory");
+  }
+  if (lane == 0) out[wave] = bad;
+}
+
+// What a block's worth of scalar loads costs by itself: every wave of the
+// workgroup sends 4 s_load_dwordx16 (256 B, one ring record), waits, and
+// repeats.  kGlc: with glc, always the same record (the ring's pattern of
+// reuse); otherwise plain loads that walk fresh memory, 256 B per turn, so
+// every load misses the scalar cache as well.  out[wave of the grid] = cycles.
+template <bool kGlc>
+__global__ __launch_bounds__(576) void k_sload(const uint8_t* base, uint32_t iters, uint64_t* out) {
+  const uint32_t wave = rfl_u32(threadIdx.x >> 6);
+  const uint32_t gw = blockIdx.x * (blockDim.x >> 6) + wave;
+  const uint8_t* p = base + (uint64_t)gw * (kGlc ? 256u : 256u * iters);
+  const uint64_t t0 = __builtin_amdgcn_s_memtime();
+  if constexpr (kGlc)
+    asm volatile(
+        "s_mov_b32 s33, %[n]\n\t"
+        "s_mov_b64 s[34:35], %[p]\n\t"
+        "1:\n\t"
+        "s_load_dwordx16 s[36:51], s[34:35], 0x0 glc\n\t"
+        "s_load_dwordx16 s[52:67], s[34:35], 0x40 glc\n\t"
+        "s_load_dwordx16 s[68:83], s[34:35], 0x80 glc\n\t"
+        "s_load_dwordx16 s[84:99], s[34:35], 0xc0 glc\n\t"
+        "s_waitcnt lgkmcnt(0)\n\t"
+        "s_add_i32 s33, s33, -1\n\t"
+        "s_cmp_lg_u32 s33, 0\n\t"
+        "s_cbranch_scc1 1b"
+        :
+        : [n] "s"(iters), [p] "s"(p)
+        : "memory", "scc", "s33", "s34", "s35", "s36", "s37", "s38", "s39", "s40", "s41", "s42",
+          "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54",
+          "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66",
+          "s67", "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78",
+          "s79", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "s90",
+          "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99");
+  else
+    asm volatile(
+        "s_mov_b32 s33, %[n]\n\t"
+        "s_mov_b64 s[34:35], %[p]\n\t"
+        "1:\n\t"
+        "s_load_dwordx16 s[36:51], s[34:35], 0x0\n\t"
+        "s_load_dwordx16 s[52:67], s[34:35], 0x40\n\t"
+        "s_load_dwordx16 s[68:83], s[34:35], 0x80\n\t"
+        "s_load_dwordx16 s[84:99], s[34:35], 0xc0\n\t"
+        "s_waitcnt lgkmcnt(0)\n\t"
+        "s_add_u32 s34, s34, 0x100\n\t"
+        "s_addc_u32 s35, s35, 0\n\t"
+        "s_add_i32 s33, s33, -1\n\t"
+        "s_cmp_lg_u32 s33, 0\n\t"
+        "s_cbranch_scc1 1b"
+        :
+        : [n] "s"(iters), [p] "s"(p)
+        : "memory", "scc", "s33", "s34", "s35", "s36", "s37", "s38", "s39", "s40", "s41", "s42",
+          "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54",
+          "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66",
+          "s67", "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78",
+          "s79", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "s90",
+          "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99");
+  const uint64_t t1 = __builtin_amdgcn_s_memtime();
+  if ((threadIdx.x & 63u) == 0) out[gw] = t1 - t0;
+}
+
+template <bool kGlc>
+static void run_sload(int groups, int waves, uint32_t iters) {
+  const size_t nw = (size_t)groups * waves;
+  const size_t bytes = nw * 256u * (kGlc ? 1u : iters);
+  uint8_t* d;
+  uint64_t* d_out;
+  CK(hipMalloc(&d, bytes));
+  CK(hipMemset(d, 1, bytes));
+  CK(hipMalloc(&d_out, nw * sizeof(uint64_t)));
+  CK(hipDeviceSynchronize());
+  hipLaunchKernelGGL(k_sload<kGlc>, dim3(groups), dim3(waves * 64), 0, 0, d, iters, d_out);
+  CK(hipGetLastError());
+  CK(hipDeviceSynchronize());
+  std::vector<uint64_t> h(nw);
+  CK(hipMemcpy(h.data(), d_out, nw * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  std::sort(h.begin(), h.end());
+  printf("sload[%s] %d workgroups x %d waves: %.0f cycles (s_memtime) per 4 x dwordx16, median wave; %.0f slowest\n",
+         kGlc ? "glc, one record" : "plain, fresh memory", groups, waves,
+         (double)h[nw / 2] / iters, (double)h[nw - 1] / iters);
+  CK(hipFree(d));
+  CK(hipFree(d_out));
+}
+
+template <bool kFence>
+static int run_sf_probe(uint32_t laps) {
+  uint8_t* raw;
+  uint32_t* d_out;
+  CK(hipMalloc(&raw, (kSfChains + 1) * kSfRingBytes));
+  CK(hipMalloc(&d_out, sizeof(uint32_t) * kSfChains));
+  CK(hipMemset(raw, 0, (kSfChains + 1) * kSfRingBytes));
+  CK(hipMemset(d_out, 0xff, sizeof(uint32_t) * kSfChains));
+  uint8_t* ring = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(raw) + kSfRingBytes - 1) &
+                                             ~uintptr_t(kSfRingBytes - 1));
+  hipLaunchKernelGGL(k_sf_probe<kFence>, dim3(1), dim3(kSfThreads), 0, 0, ring, laps, d_out);
+  CK(hipGetLastError());
+  CK(hipDeviceSynchronize());
+  uint32_t h[kSfChains];
+  CK(hipMemcpy(h, d_out, sizeof(h), hipMemcpyDeviceToHost));
+  uint64_t bad = 0;
+  for (int w = 0; w < kSfChains; ++w) bad += h[w];
+  printf("sf_probe[%s] %u laps x %d chains x %u dwords: %llu mismatches\n",
+         kFence ? "release fence (agent) + vmcnt(0)" : "vmcnt(0) alone", laps, kSfChains,
+         kSfHalf * 64u, (unsigned long long)bad);
+  CK(hipFree(raw));
+  CK(hipFree(d_out));
+  return bad ? 1 : 0;
+}
+
 // chain_phase with the 16 LDS reads of block h+1 spread through block h's 256
 // VALU (one read per kR VALU, placed with sched_group_barrier) instead of
 // issued together at the block's start.
@@ -571,6 +757,64 @@ __global__ void k_md5_step4(uint64_t* out, uint32_t* sink, int iters) {
   sink[threadIdx.x] = a + b + c + d;
 }
 
+// The same step in every wave of one workgroup, `active` lanes live, mk in a
+// VGPR or in an SGPR: out[wave] = that wave's cycles (run_step_feed prints the
+// slowest wave; run_issue's kernels time wave 0 only).
+template <bool kSgpr>
+__global__ void k_step_feed(uint64_t* out, uint32_t* sink, int iters, uint32_t active) {
+  uint32_t a = threadIdx.x, b = 1, c = 2, d = 3;
+  const uint32_t mk = 7;
+  uint64_t t0 = 0, t1 = 0;
+  if ((threadIdx.x & 63u) < active) {
+    t0 = __builtin_amdgcn_s_memtime();
+    for (int i = 0; i < iters; ++i) {
+      if constexpr (kSgpr)
+        asm volatile(REP8(REP8(
+            "v_bitop3_b32 %0, %1, %2, %3 bitop3:0xca\n"
+            "v_add3_u32 %0, %0, %4, %1\n"
+            "v_alignbit_b32 %0, %0, %0, 25\n"
+            "v_add_u32 %0, %0, %1\n"))
+                     : "+v"(a), "+v"(b), "+v"(c), "+v"(d)
+                     : "s"(mk));
+      else
+        asm volatile(REP8(REP8(
+            "v_bitop3_b32 %0, %1, %2, %3 bitop3:0xca\n"
+            "v_add3_u32 %0, %0, %4, %1\n"
+            "v_alignbit_b32 %0, %0, %0, 25\n"
+            "v_add_u32 %0, %0, %1\n"))
+                     : "+v"(a), "+v"(b), "+v"(c), "+v"(d)
+                     : "v"(mk));
+    }
+    t1 = __builtin_amdgcn_s_memtime();
+  }
+  if ((threadIdx.x & 63u) == 0) out[threadIdx.x >> 6] = t1 - t0;
+  sink[threadIdx.x] = a + b + c + d;
+}
+
+template <bool kSgpr>
+static void run_step_feed(int waves, uint32_t active, int iters) {
+  uint64_t* d_out;
+  uint32_t* d_sink;
+  CK(hipMalloc(&d_out, 8 * 16));
+  CK(hipMalloc(&d_sink, 4 * 1024));
+  hipLaunchKernelGGL(k_step_feed<kSgpr>, dim3(1), dim3(waves * 64), 0, 0, d_out, d_sink, 10, active);
+  CK(hipDeviceSynchronize());
+  hipLaunchKernelGGL(k_step_feed<kSgpr>, dim3(1), dim3(waves * 64), 0, 0, d_out, d_sink, iters, active);
+  CK(hipDeviceSynchronize());
+  uint64_t h[16];
+  CK(hipMemcpy(h, d_out, 8 * waves, hipMemcpyDeviceToHost));
+  uint64_t lo = h[0], hi = h[0];
+  for (int w = 1; w < waves; ++w) {
+    lo = std::min(lo, h[w]);
+    hi = std::max(hi, h[w]);
+  }
+  printf("  md5 step4, mk in %s, %2u lanes live, %d waves/WG: %.2f .. %.2f cycles per instr (fastest .. slowest wave)\n",
+         kSgpr ? "SGPR" : "VGPR", active, waves, (double)lo / ((double)iters * 256),
+         (double)hi / ((double)iters * 256));
+  CK(hipFree(d_out));
+  CK(hipFree(d_sink));
+}
+
 // VALU + ds_read_b128 interleaved (1 LDS read per 4 VALU, as the chain wave).
 __global__ void k_mix_lds(uint64_t* out, uint32_t* sink, int iters) {
   __shared__ u32x4 lds[64];
@@ -802,8 +1046,41 @@ static void run_md5(int B, uint64_t L, int reps, bool check, int which = 0, uint
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
   const int grid = (B + 63) / 64;
+  // scalar-fed kernels (which 60..70): one ring of kSfRingBytes per chain
+  const int sf_chains = which == 62 ? 8 : which == 66 ? 1 : which == 67 ? 2 : which == 68 ? 4 : kSfChains;
+  const int sf_grid = (B + sf_chains - 1) / sf_chains;
+  uint8_t* d_ring_raw = nullptr;
+  uint8_t* d_ring = nullptr;
+  if (which >= 60 && which <= 70) {
+    CK(hipMalloc(&d_ring_raw, ((size_t)sf_grid * sf_chains + 1) * kSfRingBytes));
+    d_ring = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(d_ring_raw) + kSfRingBytes - 1) &
+                                        ~uintptr_t(kSfRingBytes - 1));
+  }
   auto launch = [&]() {
-    if (which == 0)
+    if (which == 60)
+      hipLaunchKernelGGL(qsmd5_batch_sf_kernel, dim3(sf_grid), dim3(kSfThreads), 0, 0, d_desc,
+                         nullptr, (uint32_t)B, d_dig, g_skew, d_ring);
+    else if (which == 61)
+      hipLaunchKernelGGL(k_sf<true>, dim3(sf_grid), dim3(kSfThreads), 0, 0, d_desc, nullptr,
+                         (uint32_t)B, d_dig, g_skew, d_ring);
+    else if (which >= 63 && which <= 65)
+      hipLaunchKernelGGL(which == 63 ? k_sf_attrib<1> : which == 64 ? k_sf_attrib<2> : k_sf_attrib<3>,
+                         dim3(sf_grid), dim3(kSfThreads), 0, 0, d_desc, nullptr, (uint32_t)B, d_dig,
+                         g_skew, d_ring);
+    else if (which == 62)
+      hipLaunchKernelGGL(k_sfc<8>, dim3(sf_grid), dim3(576), 0, 0, d_desc, nullptr, (uint32_t)B,
+                         d_dig, g_skew, d_ring);
+    else if (which == 66)
+      hipLaunchKernelGGL(k_sfc<1>, dim3(sf_grid), dim3(128), 0, 0, d_desc, nullptr, (uint32_t)B,
+                         d_dig, g_skew, d_ring);
+    else if (which == 67)
+      hipLaunchKernelGGL(k_sfc<2>, dim3(sf_grid), dim3(192), 0, 0, d_desc, nullptr, (uint32_t)B,
+                         d_dig, g_skew, d_ring);
+    else if (which == 68)
+      hipLaunchKernelGGL(k_sfc<4>, dim3(sf_grid), dim3(320), 0, 0, d_desc, nullptr, (uint32_t)B,
+                         d_dig, g_skew, d_ring);
+
+    else if (which == 0)
       hipLaunchKernelGGL(qsmd5_batch_kernel, dim3(grid), dim3(64), 0, 0, d_desc, nullptr,
                          (uint32_t)B, d_dig);
     else if (which == 1)  // what the runtime launches at 64 chains per workgroup
@@ -929,7 +1206,7 @@ static void run_md5(int B, uint64_t L, int reps, bool check, int which = 0, uint
   if (g_host_pinned) printf("[pinned host, zero-copy] ");
   printf("md5[%s] B=%d L=%llu: median %.3f ms best %.3f ms -> %.2f GiB/s total, r1=%.4f GiB/s/chain, "
          "%.1f cycles/block @2.4GHz\n",
-         which == 0 ? "v1" : which == 1 ? "pc" : which == 2 ? "coal" : which == 3 ? "pc-d2" : which == 5 ? "pc-h2" : which == 6 ? "coal-imm" : which == 19 ? "pc (runtime lanes)" : which == 20 ? "pc-r1 (depth 1, no pause)" : which == 21 ? "pace8" : which == 22 ? "pace10" : which == 23 ? "d2-pace8" : which == 24 ? "d2-pace16" : which == 25 ? "d2-pace24" : which == 26 ? "d2-pace32" : which == 30 ? "lead8" : which == 31 ? "lead8+24" : which == 32 ? "lead4+16" : which == 33 ? "lead8+32" : which == 34 ? "lead0 (no graded wait)" : which == 40 ? "pc2 d1 (64u fixed)" : which == 41 ? "pc2 d2" : which == 42 ? "pc2 d2 pace4" : which == 43 ? "pc2 d2 pace8" : which == 44 ? "pc2 d2 pace2" : which == 35 ? "lead8 pace4" : which == 36 ? "lead8 pace12" : which == 37 ? "lead8 pace8 depth3" : which == 38 ? "lead8 pace16 depth3" : which == 39 ? "lead8 no pause" : which == 50 ? "probe: producer writes no ring" : which == 51 ? "probe: producer loads nothing" : which == 52 ? "probe: producer neither loads nor writes" : "pc-d3", B, (unsigned long long)L, med, best, gib / (med / 1e3), (double)L / (1u << 30) / (med / 1e3),
+         which == 0 ? "v1" : which == 1 ? "pc" : which == 2 ? "coal" : which == 3 ? "pc-d2" : which == 5 ? "pc-h2" : which == 6 ? "coal-imm" : which == 19 ? "pc (runtime lanes)" : which == 20 ? "pc-r1 (depth 1, no pause)" : which == 21 ? "pace8" : which == 22 ? "pace10" : which == 23 ? "d2-pace8" : which == 24 ? "d2-pace16" : which == 25 ? "d2-pace24" : which == 26 ? "d2-pace32" : which == 30 ? "lead8" : which == 31 ? "lead8+24" : which == 32 ? "lead4+16" : which == 33 ? "lead8+32" : which == 34 ? "lead0 (no graded wait)" : which == 40 ? "pc2 d1 (64u fixed)" : which == 41 ? "pc2 d2" : which == 42 ? "pc2 d2 pace4" : which == 43 ? "pc2 d2 pace8" : which == 44 ? "pc2 d2 pace2" : which == 35 ? "lead8 pace4" : which == 36 ? "lead8 pace12" : which == 37 ? "lead8 pace8 depth3" : which == 38 ? "lead8 pace16 depth3" : which == 39 ? "lead8 no pause" : which == 50 ? "probe: producer writes no ring" : which == 51 ? "probe: producer loads nothing" : which == 52 ? "probe: producer neither loads nor writes" : which == 60 ? "sf (scalar-fed)" : which == 61 ? "sf, agent release fence" : which == 62 ? "sf, 8 chains per workgroup" : which == 66 ? "sf, 1 chain per workgroup" : which == 67 ? "sf, 2 chains per workgroup" : which == 68 ? "sf, 4 chains per workgroup" : which == 63 ? "sf probe: producer writes no ring" : which == 64 ? "sf probe: producer loads nothing" : which == 65 ? "sf probe: producer neither loads nor writes" : "pc-d3", B, (unsigned long long)L, med, best, gib / (med / 1e3), (double)L / (1u << 30) / (med / 1e3),
          (med / 1e3) * 2.4e9 / (double)(L / 64));
   if (check) {
     std::vector<uint32_t> dig(4 * (size_t)B);
@@ -959,13 +1236,15 @@ static void run_md5(int B, uint64_t L, int reps, bool check, int which = 0, uint
     printf("  check %d chunks: %s\n", ncheck, bad ? "FAIL" : "ok");
   }
   if (g_host_pinned) CK(hipHostFree(d_data)); else CK(hipFree(d_data));
+  if (d_ring_raw) CK(hipFree(d_ring_raw));
   CK(hipFree(d_desc));
   CK(hipFree(d_dig));
 }
 
 // Edge lengths on unaligned offsets, 1 launch each, all checked.
 static int run_edges(int which) {
-  const uint64_t lens[] = {0, 1, 3, 55, 56, 57, 63, 64, 65, 119, 120, 127, 128, 1000, 4096, 8191, 100003};
+  const uint64_t lens[] = {0, 1, 3, 55, 56, 57, 63, 64, 65, 119, 120, 127, 128, 511, 512, 513, 1000,
+                           1024, 1093, 1600, 4096, 8191, 100003};
   const int nl = sizeof(lens) / sizeof(lens[0]);
   int bad = 0;
   uint8_t* d;
@@ -988,7 +1267,15 @@ static int run_edges(int which) {
   CK(hipMalloc(&dg, 16 * n));
   CK(hipMemcpy(dd, desc.data(), sizeof(ChunkDesc) * n, hipMemcpyHostToDevice));
   CK(hipMemset(dg, 0, 16 * n));
-  if (which == 0)
+  uint8_t* ring_raw = nullptr;
+  if (which == 60) {
+    const size_t chains = (size_t)(n + kSfChains - 1) / kSfChains * kSfChains;
+    CK(hipMalloc(&ring_raw, (chains + 1) * kSfRingBytes));
+    uint8_t* ring = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(ring_raw) + kSfRingBytes - 1) &
+                                               ~uintptr_t(kSfRingBytes - 1));
+    hipLaunchKernelGGL(qsmd5_batch_sf_kernel, dim3((n + kSfChains - 1) / kSfChains),
+                       dim3(kSfThreads), 0, 0, dd, nullptr, (uint32_t)n, dg, g_skew, ring);
+  } else if (which == 0)
     hipLaunchKernelGGL(qsmd5_batch_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, dd, nullptr,
                        (uint32_t)n, dg);
   else if (which == 1)
@@ -1038,6 +1325,7 @@ static int run_edges(int which) {
     }
   }
   printf("edges[%d]: %d cases, %d bad\n", which, n, bad);
+  if (ring_raw) CK(hipFree(ring_raw));
   CK(hipFree(d));
   CK(hipFree(dd));
   CK(hipFree(dg));
@@ -1774,6 +2062,50 @@ int main(int argc, char** argv) {
     // 2048 workgroups = exactly 8 on each of 256 CUs)
     for (uint32_t extra : {0u, 4096u})
       for (uint64_t kib : {64, 256}) run_stamps(131072, kib << 10, 6, 4352, extra);
+    return 0;
+  }
+  if (!strcmp(mode, "sf_probe")) {  // does a glc scalar load see the same workgroup's fresh stores?
+    const uint32_t laps = argc > 2 ? (uint32_t)atoi(argv[2]) : 4096u;
+    return run_sf_probe<false>(laps) + run_sf_probe<true>(laps);
+  }
+  if (!strcmp(mode, "step_feed")) {  // does an SGPR operand, or one live lane, change the step's rate?
+    for (int waves : {1, 2, 4, 8})
+      for (uint32_t active : {64u, 1u}) {
+        run_step_feed<false>(waves, active, 4000);
+        run_step_feed<true>(waves, active, 4000);
+      }
+    return 0;
+  }
+  if (!strcmp(mode, "sload")) {  // what the scalar feed's loads cost without any VALU beside them
+    for (int waves : {1, 2, 4, 8}) run_sload<true>(1, waves, 4096);
+    run_sload<true>(64, 8, 4096);
+    for (int waves : {1, 2, 4, 8}) run_sload<false>(1, waves, 4096);
+    run_sload<false>(64, 8, 4096);
+    return 0;
+  }
+  if (!strcmp(mode, "sf")) {  // scalar-fed against LDS-fed latency kernel, alternating
+    int bad = run_edges(60);
+    if (bad) return 1;
+    for (int r = 0; r < 3; ++r) {
+      run_md5(512, 10485760, 3, r == 0, 1);
+      run_md5(512, 10485760, 3, r == 0, 60);
+    }
+    run_md5(512, 10485760, 3, true, 61);
+    run_md5(512, 10485760, 3, true, 62);
+    return 0;
+  }
+  if (!strcmp(mode, "sf_attrib")) {  // what the producer's loads and ring writes cost the chains
+    for (int w : {60, 63, 64, 65}) run_md5(512, 10485760, 2, false, w);
+    return 0;
+  }
+  if (!strcmp(mode, "sf_chains")) {  // chain waves per workgroup
+    for (int w : {1, 66, 67, 60, 68, 62}) run_md5(512, 10485760, 2, true, w);
+    run_md5(256, 10485760, 2, true, 66);
+    return 0;
+  }
+  if (!strcmp(mode, "sf_nmax")) {  // where the lane-packed kernel takes over again
+    for (int B : {512, 768, 1024, 2048, 4096})
+      for (int w : {1, 60}) run_md5(B, 10485760, 2, B <= 1024, w);
     return 0;
   }
   if (!strcmp(mode, "sat")) {
